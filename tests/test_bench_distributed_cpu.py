@@ -100,34 +100,47 @@ SCRIPT = textwrap.dedent("""
     allt = [torch.empty_like(t) for _ in range(w)]
     dist.all_gather(allt, t)
     assert max(float(x) for x in allt) == float(w)
-    dist.barrier()
+    dist.monitored_barrier()     # (gloo's CPU barrier: dist.barrier() would ask the HIP runtime for an accelerator)
     dist.destroy_process_group()
     print("rank", r, "ok")
 """) % ROOT
 
 
-def test_two_rank_gloo(tmp_path):
-    f = tmp_path / "w2.py"
+def run_ranks(tmp_path, world, port):
+    """Starts `world` ranks of SCRIPT with the environment torch.distributed.run gives its workers (env:// rendezvous) and
+    returns their joined stdout.  The ranks are started directly: the launcher asks the HIP runtime for the machine's devices,
+    which on a GPU machine makes it one more process holding the GPU, and these CPU ranks never use one."""
+    f = tmp_path / ("w%d.py" % world)
     f.write_text(SCRIPT)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-                          "--master-addr", "127.0.0.1", "--master-port", "29517", str(f)],
-                         capture_output=True, text=True, env=env, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.count("ok") == 2
+    base = dict(os.environ, OMP_NUM_THREADS="1")
+    base.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world))
+    procs = []
+    for r in range(world):
+        out, err = open(tmp_path / ("r%d.out" % r), "w"), open(tmp_path / ("r%d.err" % r), "w")
+        procs.append((subprocess.Popen([sys.executable, str(f)], stdout=out, stderr=err, text=True,
+                                       env=dict(base, RANK=str(r), LOCAL_RANK=str(r))), out, err))
+    rcs = []
+    for p, out, err in procs:
+        try:
+            rcs.append(p.wait(timeout=600))
+        except subprocess.TimeoutExpired:
+            p.kill()
+            rcs.append(p.wait())
+        out.close()
+        err.close()
+    logs = "".join((tmp_path / ("r%d.out" % r)).read_text() + (tmp_path / ("r%d.err" % r)).read_text() for r in range(world))
+    assert rcs == [0] * world, logs[-5000:]
+    return "".join((tmp_path / ("r%d.out" % r)).read_text() for r in range(world))
+
+
+def test_two_rank_gloo(tmp_path):
+    assert run_ranks(tmp_path, 2, 29517).count("ok") == 2
 
 
 def test_eight_rank_gloo(tmp_path):
     """The 8-way split a driver with an 8-GPU node will run (no such node here): 64 problems -> 8 per rank, p -> rank p mod 8,
     gathered [64, m] on rank 0, max-over-ranks timing reduction -- the same batch.py functions, 8 gloo ranks on the CPU."""
-    f = tmp_path / "w8.py"
-    f.write_text(SCRIPT)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
-    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
-                          "--master-addr", "127.0.0.1", "--master-port", "29519", str(f)],
-                         capture_output=True, text=True, env=env, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.count("ok") == 8
+    assert run_ranks(tmp_path, 8, 29519).count("ok") == 8
 
 
 def test_bench_uses_the_batch_module():
@@ -148,3 +161,12 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert "--gpus 4 but WORLD_SIZE=1" in (out.stdout + out.stderr)
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "torch.distributed.run" in src and "args.gpus" in src
+
+
+def test_bench_refuses_a_step_count_below_one():
+    """--steps is the number of timed steps: zero (nothing timed, a rate of 0 / 0) is refused before a GPU is touched."""
+    envv = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300,
+                         env=envv)
+    assert out.returncode != 0
+    assert "--steps must be >= 1" in out.stderr

@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from eigensolver_gpu_amd import api
 torch.cuda.set_device(0)
