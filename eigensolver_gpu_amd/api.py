@@ -39,7 +39,8 @@ EXPORTS = [
     "eigsolve_zher2k", "eigsolve_dsyr2k", "eigsolve_zher2k_bench", "eigsolve_dsyr2k_bench", "eigsolve_ztrsm_lun",
     "eigsolve_dtrsm_lun", "eigsolve_version", "eigsolve_zhetrd_mv_sweep", "eigsolve_dsytrd_mv_sweep", "eigsolve_zhetrd_her2k_sweep", "eigsolve_dsytrd_her2k_sweep",
     "eigsolve_dstedc_device", "eigsolve_zlarft", "eigsolve_dlarft", "eigsolve_zunmtr", "eigsolve_dormtr",
-    "eigsolve_zhegvdx_batch", "eigsolve_dsygvdx_batch",
+    "eigsolve_zhegvdx_batch", "eigsolve_dsygvdx_batch", "eigsolve_zhegvdx_ex", "eigsolve_dsygvdx_ex", "eigsolve_zhegst_ex",
+    "eigsolve_dsygst_ex", "eigsolve_dstebz_device",
 ]
 
 
@@ -213,6 +214,33 @@ def hegvdx(A_d, B_d, il, iu, ws=None, skip_host_copy=False):
     return info, ws
 
 
+def hegvdx_ex(A_d, B_d, itype=1, jobz="V", range="I", vl=0.0, vu=0.0, il=1, iu=None, ws=None, Z_d=None):
+    """Extended driver (eigsolve_zhegvdx_ex / eigsolve_dsygvdx_ex): itype 1 (A x = l B x), 2 (A B x = l x), 3 (B A x = l x);
+    jobz 'N' / 'V'; range 'A', 'V' ((vl, vu]) or 'I' (il..iu, iu=None: N).  A_d, B_d column-major device tensors (shape
+    (N, ld)), overwritten as by `hegvdx`.  Uses the device parts of `ws` (a Workspace; its Z unless Z_d is given).
+    Returns (info, meig, w_d[:meig], Z[:meig] or None) -- Z[:meig] are the first meig columns (column-major view)."""
+    import torch
+    _sync()
+    N = A_d.shape[0]
+    cx = A_d.dtype == torch.complex128
+    if ws is None:
+        ws = Workspace(N, cx)
+    if iu is None:
+        iu = N
+    Z = (ws.Z if Z_d is None else Z_d) if jobz == "V" else Z_d
+    ldz = Z.shape[1] if Z is not None else 1
+    info, meig = c_int(0), c_int(0)
+    args = [c_int(itype), ctypes.c_char(jobz.encode()), ctypes.c_char(range.encode()), c_int(N), _p(A_d), c_int(A_d.shape[1]),
+            _p(B_d), c_int(B_d.shape[1]), ctypes.c_double(vl), ctypes.c_double(vu), c_int(il), c_int(iu), ctypes.byref(meig),
+            _p(ws.w), _p(Z), c_int(ldz), _p(ws.work), c_int(ws.lwork)]
+    if cx:
+        lib().eigsolve_zhegvdx_ex(*args, _p(ws.rwork), c_int(ws.lrwork), ctypes.byref(info))
+    else:
+        lib().eigsolve_dsygvdx_ex(*args, ctypes.byref(info))
+    m = meig.value
+    return info.value, m, ws.w[:m], (Z[:m] if Z is not None and jobz == "V" else None)
+
+
 def hegvdx_batch(pairs, il, iu, wss, skip_host_copy=False, null_entry=None):
     """nprob problems of ONE order and type in one call (eigsolve_zhegvdx_batch / eigsolve_dsygvdx_batch): the library keeps
     `batch_workers` of them in flight on its own worker threads (option 0: lockstep tridiagonalizations on the caller's
@@ -299,6 +327,14 @@ def hegst(A_d, U_d):
     name = "eigsolve_zhegst" if _pre(A_d) == "z" else "eigsolve_dsygst"
     rc = getattr(lib(), name)(c_int(N), _p(A_d), c_int(A_d.shape[1]), _p(U_d), c_int(U_d.shape[1]), c_int(448))
     assert rc == 0
+
+
+def hegst_ex(itype, A_d, U_d):
+    """LAPACK ?hegst ('U') in place on A_d: itype 1 A <- U^-H A U^-1, itype 2 / 3 A <- U A U^H.  Returns the status."""
+    _sync()
+    N = A_d.shape[0]
+    name = "eigsolve_zhegst_ex" if _pre(A_d) == "z" else "eigsolve_dsygst_ex"
+    return getattr(lib(), name)(c_int(itype), c_int(N), _p(A_d), c_int(A_d.shape[1]), _p(U_d), c_int(U_d.shape[1]))
 
 
 def hetrd(A_d, nb=0):
@@ -472,6 +508,21 @@ def stedc_device(d, e):
     ms = ctypes.c_double(0)
     rc = lib().eigsolve_dstedc_device(c_int(N), _p(dd), _p(ed), _p(w), _p(Q), c_int(N), ctypes.byref(ms))
     return rc, w.cpu().numpy(), to_host(Q), ms.value
+
+
+def stebz_device(d, e, range="A", vl=0.0, vu=0.0, il=1, iu=None):
+    """Device bisection on a symmetric tridiagonal (numpy d[N], e[N-1]) -> (rc, w[:m], ms): range 'A', 'V' ((vl, vu]), 'I'."""
+    import torch
+    _sync()
+    N = len(d)
+    dd = torch.from_numpy(np.ascontiguousarray(d, dtype=np.float64)).cuda()
+    ed = torch.from_numpy(np.ascontiguousarray(np.r_[e, 0.0], dtype=np.float64)).cuda()
+    w = torch.zeros(max(N, 1), dtype=torch.float64, device="cuda")
+    m, ms = c_int(0), ctypes.c_double(0)
+    rc = lib().eigsolve_dstebz_device(c_int(N), _p(dd), _p(ed), ctypes.c_char(range.encode()), ctypes.c_double(vl),
+                                      ctypes.c_double(vu), c_int(il), c_int(N if iu is None else iu), ctypes.byref(m), _p(w),
+                                      ctypes.byref(ms))
+    return rc, w[: m.value].cpu().numpy(), ms.value
 
 
 def heevd(A_d, il, iu, ws=None):

@@ -152,6 +152,10 @@ template <class T> void build_inv_blocks(Ctx& c, hipStream_t st, int N, const T*
 
 // A <- U^-H A U^-1 (upper triangle only is read/written).
 template <class T> void hegst_upper(Ctx& c, hipStream_t st, int N, T* A, int lda, const T* U, int ldu);
+// A <- U A U^H (itype 2 and 3; upper triangle only is read/written; scratch F, G of hegst).
+template <class T> void hegst_upper_itype23(Ctx& c, hipStream_t st, int N, T* A, int lda, const T* U, int ldu);
+// Y = U^H X (n x m), out of place, U upper (the back-transformation of itype 3).
+template <class T> void trmm_LUC(Ctx& c, hipStream_t st, int n, int m, const T* U, int ldu, const T* X, int ldx, T* Y, int ldy);
 
 // potrf(B) || hegst(A, U) pipeline (option "overlap" bit 0; see blas3.hip): *_begin enqueues the whole factorization on
 // c.s1 and the steps of hegst's top level that only need the leading half of the factor on the second stream; the caller

@@ -2657,6 +2657,32 @@ template <class T> void hegst_two_solves(Ctx& c, hipStream_t st, int N, T* A, in
     hegst_two_solves_at(c, st, N, 0, A, lda, U, ldu);
 }
 
+// ---- itype 2 / 3 (A B x = lambda x, B A x = lambda x): C = U A U^H, two products ----------------------------------------------
+// F = Herm(A), G = U F (triangular operand: trim_k skips its zero half), upper(A) <- upper(G U^H).  (4/3) N^3 multiply-adds in two
+// chip-filling launches (the symmetric recursion of LAPACK's zhegst needs N^3 in ~16 N / 64 small ones).  Scratch: hegst's F and G.
+template <class T> void hegst_upper_itype23(Ctx& c, hipStream_t st, int N, T* A, int lda, const T* U, int ldu) {
+    if (N <= 0) return;
+    T* F = c.scratch<T>(Tr<T>::cx ? "gst_Fz" : "gst_Fd", (size_t)N * N);
+    T* G = c.scratch<T>(Tr<T>::cx ? "gst_Gz" : "gst_Gd", (size_t)N * N);
+    const int nb32 = (N + 31) / 32;
+    klaunch(c, st, (herm_complete_kernel<T>), dim3(nb32, nb32), dim3(256), N, (const T*)A, lda, F, N);
+    Operand<T> Uo = opA('N', U, ldu);
+    Uo.mask = M_UPPER;
+    gemm<T>(c, st, N, N, N, Tr<T>::one(), Uo, opB('N', (const T*)F, N), Tr<T>::zero(), G, N);          // G = U F
+    Operand<T> Uh = opB('C', U, ldu);
+    Uh.mask = M_UPPER;
+    Epi e; e.uplo = 1; e.herm_diag = 1;
+    gemm<T>(c, st, N, N, N, Tr<T>::one(), opA('N', (const T*)G, N), Uh, Tr<T>::zero(), A, lda, e);    // upper(A) = upper(G U^H)
+    EIG_HIP(hipGetLastError());
+}
+
+template <class T> void trmm_LUC(Ctx& c, hipStream_t st, int n, int m, const T* U, int ldu, const T* X, int ldx, T* Y, int ldy) {
+    if (n <= 0 || m <= 0) return;
+    Operand<T> Uh = op_plain(U, ldu, 1, 1);   // U^H(i, k) = conj(U(k, i)), stored (k, i): upper
+    Uh.mask = M_UPPER;
+    gemm<T>(c, st, n, m, n, Tr<T>::one(), Uh, opB('N', X, ldx), Tr<T>::zero(), Y, ldy);
+}
+
 // The block step of the symmetric algorithm (zhegst_gpu.F90:85-104) for the leading block [k0, k0+n1) against the n2
 // columns to its right, A11 already reduced:
 //     A12 <- U11^-H A12                      (:87-88)
@@ -2964,6 +2990,8 @@ template void two_stage_stage1_skeleton<double>(Ctx&, hipStream_t, int, int);
     template void build_inv256<T>(Ctx&, hipStream_t, int, const T*, int);                                                \
     template void build_inv_blocks<T>(Ctx&, hipStream_t, int, const T*, int);                                            \
     template void hegst_upper<T>(Ctx&, hipStream_t, int, T*, int, const T*, int);                                        \
+    template void hegst_upper_itype23<T>(Ctx&, hipStream_t, int, T*, int, const T*, int);                                \
+    template void trmm_LUC<T>(Ctx&, hipStream_t, int, int, const T*, int, const T*, int, T*, int);                       \
     template void potrf_upper_group<T>(Ctx&, hipStream_t, int, int, T* const*, int);                                     \
     template bool pipeline_applicable<T>(const Ctx&, int);                                                               \
     template void potrf_hegst_pipelined_begin<T>(Ctx&, int, T*, int, T*, int);                                           \

@@ -9,6 +9,7 @@
 
 #include <climits>
 #include "../../include/eigsolve_gpu.h"
+#include "stebz.h"
 #include "stedc.h"
 #include "trd.h"
 
@@ -266,15 +267,24 @@ struct PhaseTimer {
     }
 };
 
+// range = 'V' of the extended driver: (vl, vu] in, the index range il..iu it selects out (il > iu: none)
+struct ValueRange {
+    double vl, vu;
+    int il, iu;
+};
+
 // ---- heevd: trd -> host dstedc -> upload wanted vectors -> back-transform -----------------------
 // e_d/tau_d/W_d: device workspace pieces.  e_h[N], Q_h (N x N, ldq), swork/lswork, iwork: host.
+// w_h == nullptr: no host copy of the eigenvalues (device tridiagonal solver only).  vr != nullptr (device tridiagonal solver only):
+// il..iu are replaced by the index range of (vr->vl, vr->vu] from two Sturm counts on T; when it is empty nothing after the
+// tridiagonalization runs.
 template <class T>
 static int heevd_core(Ctx& c, int il, int iu, int N, T* A, int lda, T* Z, int ldz, double* w_d, double* e_d, T* tau_d,
                       T* W_d, double* w_h, double* e_h, double* Q_h, int ldq, double* swork, long lswork, int* iwork,
-                      int liwork) {
+                      int liwork, ValueRange* vr = nullptr) {
     hipStream_t st = c.s1;
     PhaseTimer pt(c);
-    const int m = iu - il + 1;
+    int m = iu - il + 1;
     // The real reference path copies the eigenvectors from column 1 whatever il is (dsyevd_gpu.F90:108; the complex path
     // honours il, zheevd_gpu.F90:110).  Default: honour il in both; option "real_il_reference" = 1 reproduces the quirk.
     if (!Tr<T>::cx && c.real_il_reference) { iu = iu - il + 1; il = 1; }
@@ -353,6 +363,12 @@ static int heevd_core(Ctx& c, int il, int iu, int N, T* A, int lda, T* Z, int ld
         // device-side divide & conquer: no N x N host round trip at all
         c.sync(st);
         pt.collect(PH_TRD);
+        if (vr) {
+            stebz_prepare(c, st, N, w_d, e_d);
+            stebz_value_range(c, st, N, vr->vl, vr->vu, &vr->il, &vr->iu);
+            il = vr->il; iu = vr->iu; m = iu - il + 1;
+            if (m <= 0) return 0;
+        }
         if (ovT) build_T_beside();
         double t0 = now_ms();
         double* Qd = nullptr;
@@ -365,7 +381,7 @@ static int heevd_core(Ctx& c, int il, int iu, int N, T* A, int lda, T* Z, int ld
         size_t tot = (size_t)N * m;
         hipLaunchKernelGGL((widen_kernel<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, N, m,
                            (const double*)(Qd + (size_t)(il - 1) * ldq_d), ldq_d, Z, ldz);
-        EIG_HIP(hipMemcpyAsync(w_h, w_d, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        if (w_h) EIG_HIP(hipMemcpyAsync(w_h, w_d, sizeof(double) * N, hipMemcpyDeviceToHost, st));
         phase_mark(c, st, 2 * PH_STEDC + 1);
         c.sync(st);
         c.phase_ms[PH_STEDC] += now_ms() - t0;
@@ -425,20 +441,12 @@ static void clear_phases(Ctx& c) {
     for (double& v : c.phase_ms) v = 0.0;
 }
 
-// ---- generalized driver -----------------------------------------------------------------------------
+// ---- generalized drivers -----------------------------------------------------------------------------
+// Cholesky of B (zhegvdx_gpu.F90:135-142); pipe: potrf || the U11-only part of hegst (blas3.hip: potrf_hegst_pipelined_begin).
+// -1 and a message when B is not positive definite.
 template <class T>
-static int hegvdx_core(Ctx& c, int N, T* A, int lda, T* B, int ldb, T* Z, int ldz, int il, int iu, double* w_d, double* e_d,
-                       T* tau_d, T* W_d, double* w_h, double* e_h, double* Q_h, int ldq, double* swork, long lswork,
-                       int* iwork, int liwork, T* Z_h, int ldz_h, int skip_host_copy, const char* name) {
+static int potrf_phase(Ctx& c, PhaseTimer& pt, bool pipe, int N, T* A, int lda, T* B, int ldb, const char* name) {
     hipStream_t st = c.s1;
-    PhaseTimer pt(c);
-    clear_phases(c);
-    double t_all = now_ms();
-    const int m = iu - il + 1;
-    // potrf || the U11-only part of hegst (blas3.hip: potrf_hegst_pipelined_begin) when this solve has the device to itself;
-    // phase times: "potrf" = until the factor is complete, "gst" = what is left of hegst after that.
-    const bool pipe = (c.overlap & 1) && !c.in_batch && pipeline_applicable<T>(c, N) && streams_in_use(c.dev) <= c.own_streams();
-    // Cholesky of B (zhegvdx_gpu.F90:135-142)
     {
         PhaseRange r(Tr<T>::cx ? "cusolverdnZpotrf" : "cusolverdnDpotrf");   // the reference's range name, :134
         pt.begin(PH_POTRF);
@@ -455,6 +463,45 @@ static int hegvdx_core(Ctx& c, int N, T* A, int lda, T* B, int ldb, T* Z, int ld
         else printf(" %s error: potrf failed! (B is not positive definite, pivot %d)\n", name, c.h_info[0]);
         return -1;
     }
+    return 0;
+}
+
+// The eigenvectors of the standard problem are formed in library scratch (N x m) and the final solve writes Z = U^-1 Zs
+// out of place: no staging copies inside the solve (blas3.hip, trsm_LUN), and the caller's Z is written exactly once.
+// That copy costs sizeof(T) N m of device memory per context (C4: 1 GiB).  Beyond "zs_cap_mb" (default 4 GiB), or when the
+// device cannot provide it, the vectors are formed in the CALLER's Z instead (as the reference does) and the solve runs in column
+// chunks of *mc vectors through a smaller block: Z(:, chunk) -> Zs, Zs -> Z(:, chunk).  Returns Zs (N x *mc, ld N).
+template <class T> static T* zs_alloc(Ctx& c, int N, int m, int* mc_out) {
+    const char* zs_slot = Tr<T>::cx ? "evd_Zsz" : "evd_Zsd";
+    int mc = m;
+    T* Zs = nullptr;
+    const size_t cap_elems = (size_t)c.zs_cap_mb * 1048576 / sizeof(T);
+    if ((size_t)N * m <= cap_elems) Zs = reinterpret_cast<T*>(c.try_scratch_bytes(zs_slot, sizeof(T) * (size_t)N * m));
+    if (!Zs) {
+        mc = (int)std::min<size_t>((size_t)m, std::max<size_t>(64, cap_elems / (size_t)N / 64 * 64));
+        if (mc >= m) mc = std::max(64, ((m / 2 + 63) / 64) * 64);
+        while (!(Zs = reinterpret_cast<T*>(c.try_scratch_bytes(zs_slot, sizeof(T) * (size_t)N * mc)))) {
+            if (mc <= 64) throw HipFail{hipErrorOutOfMemory};
+            mc = std::max(64, ((mc / 2 + 63) / 64) * 64);
+        }
+    }
+    *mc_out = mc;
+    return Zs;
+}
+
+template <class T>
+static int hegvdx_core(Ctx& c, int N, T* A, int lda, T* B, int ldb, T* Z, int ldz, int il, int iu, double* w_d, double* e_d,
+                       T* tau_d, T* W_d, double* w_h, double* e_h, double* Q_h, int ldq, double* swork, long lswork,
+                       int* iwork, int liwork, T* Z_h, int ldz_h, int skip_host_copy, const char* name) {
+    hipStream_t st = c.s1;
+    PhaseTimer pt(c);
+    clear_phases(c);
+    double t_all = now_ms();
+    const int m = iu - il + 1;
+    // potrf || the U11-only part of hegst (blas3.hip: potrf_hegst_pipelined_begin) when this solve has the device to itself;
+    // phase times: "potrf" = until the factor is complete, "gst" = what is left of hegst after that.
+    const bool pipe = (c.overlap & 1) && !c.in_batch && pipeline_applicable<T>(c, N) && streams_in_use(c.dev) <= c.own_streams();
+    if (potrf_phase<T>(c, pt, pipe, N, A, lda, B, ldb, name) != 0) return -1;
     // The reference saves strict-lower(A) in Z here and restores it later (:144-152) because
     // its gst/td2 overwrite parts of it; this implementation never writes below the diagonal.
     {
@@ -465,26 +512,8 @@ static int hegvdx_core(Ctx& c, int N, T* A, int lda, T* B, int ldb, T* Z, int ld
         pt.end(PH_GST);
     }
     int info;
-    // The eigenvectors of the standard problem are formed in library scratch (N x m) and the final solve writes Z = U^-1 Zs
-    // out of place: no staging copies inside the solve (blas3.hip, trsm_LUN), and the caller's Z is written exactly once.
-    // That copy costs sizeof(T) N m of device memory per context (C4: 1 GiB).  Beyond "zs_cap_mb" (default 4 GiB), or when the
-    // device cannot provide it, the vectors are formed in the CALLER's Z instead (as the reference does) and the solve runs in column
-    // chunks of mc vectors through a smaller block: Z(:, chunk) -> Zs, Zs -> Z(:, chunk).
-    const char* zs_slot = Tr<T>::cx ? "evd_Zsz" : "evd_Zsd";
     int mc = m;
-    T* Zs = nullptr;
-    {
-        const size_t cap_elems = (size_t)c.zs_cap_mb * 1048576 / sizeof(T);
-        if ((size_t)N * m <= cap_elems) Zs = reinterpret_cast<T*>(c.try_scratch_bytes(zs_slot, sizeof(T) * (size_t)N * m));
-        if (!Zs) {
-            mc = (int)std::min<size_t>((size_t)m, std::max<size_t>(64, cap_elems / (size_t)N / 64 * 64));
-            if (mc >= m) mc = std::max(64, ((m / 2 + 63) / 64) * 64);
-            while (!(Zs = reinterpret_cast<T*>(c.try_scratch_bytes(zs_slot, sizeof(T) * (size_t)N * mc)))) {
-                if (mc <= 64) throw HipFail{hipErrorOutOfMemory};
-                mc = std::max(64, ((mc / 2 + 63) / 64) * 64);
-            }
-        }
-    }
+    T* Zs = zs_alloc<T>(c, N, m, &mc);
     const bool chunked = mc < m;
     {
         PhaseRange r(Tr<T>::cx ? "zheevd_gpu" : "dsyevd_gpu");   // :161
@@ -550,6 +579,87 @@ static int hegvdx_core(Ctx& c, int N, T* A, int lda, T* B, int ldb, T* Z, int ld
     pt.end(PH_D2H);
     c.sync(st);
     pt.collect(PH_GST); pt.collect(PH_BT); pt.collect(PH_TRSM); pt.collect(PH_D2H);
+    c.phase_ms[PH_TOTAL] = now_ms() - t_all;
+    return 0;
+}
+
+// ---- extended generalized driver: itype 1 / 2 / 3, jobz 'N' / 'V', range 'A' / 'V' / 'I' ----------------------------------
+// itype 1 (A x = l B x):   C = U^-H A U^-1, x = U^-1 y   (the launches of hegvdx_core: bit-identical results)
+// itype 2 (A B x = l x):   C = U A U^H,     x = U^-1 y
+// itype 3 (B A x = l x):   C = U A U^H,     x = U^H y
+// jobz = 'N': potrf -> reduction -> tridiagonalization -> bisection (stebz.hip); no eigenvector work at all.
+// The tridiagonal step is always on the device; no host copies.  il..iu for range 'A' are 1..N (the caller sets them).
+template <class T>
+static int hegvdx_ex_core(Ctx& c, int itype, bool vectors, char range, int N, T* A, int lda, T* B, int ldb, double vl, double vu,
+                          int il, int iu, int* meig, double* w_d, T* Z, int ldz, double* e_d, T* tau_d, T* W_d, const char* name) {
+    hipStream_t st = c.s1;
+    PhaseTimer pt(c);
+    clear_phases(c);
+    const double t_all = now_ms();
+    const bool pipe = itype == 1 && (c.overlap & 1) && !c.in_batch && pipeline_applicable<T>(c, N) &&
+                      streams_in_use(c.dev) <= c.own_streams();
+    if (potrf_phase<T>(c, pt, pipe, N, A, lda, B, ldb, name) != 0) return -1;
+    {
+        PhaseRange r(Tr<T>::cx ? "zhegst_gpu" : "dsygst_gpu");
+        pt.begin(PH_GST);
+        if (itype != 1) hegst_upper_itype23<T>(c, st, N, A, lda, B, ldb);
+        else if (pipe) hegst_pipelined_finish<T>(c, N, A, lda, (const T*)B, ldb);
+        else hegst_upper<T>(c, st, N, A, lda, B, ldb);
+        pt.end(PH_GST);
+    }
+    int m = 0;
+    if (!vectors) {
+        pt.begin(PH_TRD);
+        hetrd_upper<T>(c, st, N, A, lda, w_d, e_d, tau_d, W_d, c.trd_nb);
+        pt.end(PH_TRD);
+        pt.begin(PH_STEDC);
+        stebz_prepare(c, st, N, w_d, e_d);   // (reads d from w_d before the bisection overwrites it)
+        if (range == 'V') stebz_value_range(c, st, N, vl, vu, &il, &iu);
+        m = std::max(0, iu - il + 1);
+        stebz_index(c, st, N, il, iu, w_d);
+        pt.end(PH_STEDC);
+        c.sync(st);
+        pt.collect(PH_GST); pt.collect(PH_TRD); pt.collect(PH_STEDC);
+        *meig = m;
+        c.phase_ms[PH_TOTAL] = now_ms() - t_all;
+        return 0;
+    }
+    // range 'V': the number of vectors is known after the tridiagonalization only; Zs is planned for N (Z_d has N columns)
+    const int m_plan = range == 'V' ? N : iu - il + 1;
+    int mc = m_plan;
+    T* Zs = zs_alloc<T>(c, N, m_plan, &mc);
+    const bool chunked = mc < m_plan;
+    ValueRange vr{vl, vu, il, iu};
+    int info;
+    {
+        PhaseRange r(Tr<T>::cx ? "zheevd_gpu" : "dsyevd_gpu");
+        info = heevd_core<T>(c, range == 'V' ? 1 : il, range == 'V' ? N : iu, N, A, lda, chunked ? Z : Zs, chunked ? ldz : N, w_d, e_d,
+                             tau_d, W_d, nullptr, nullptr, nullptr, N, nullptr, 0, nullptr, 0, range == 'V' ? &vr : nullptr);
+    }
+    if (info != 0) return -1;
+    if (range == 'V') { il = vr.il; iu = vr.iu; }
+    m = std::max(0, iu - il + 1);
+    if (m > 0) {
+        PhaseRange r(itype == 3 ? (Tr<T>::cx ? "ztrmm" : "dtrmm") : (Tr<T>::cx ? "cublasZtrsm" : "cublasDtrsm"));
+        pt.begin(PH_TRSM);
+        for (int j0 = 0; j0 < m; j0 += (chunked ? mc : m)) {
+            const int wj = chunked ? std::min(mc, m - j0) : m;
+            T* Zj = Z + (size_t)j0 * ldz;
+            if (chunked) EIG_HIP(hipMemcpy2DAsync(Zs, sizeof(T) * N, Zj, sizeof(T) * ldz, sizeof(T) * N, wj, hipMemcpyDeviceToDevice, st));
+            if (itype == 3) trmm_LUC<T>(c, st, N, wj, B, ldb, Zs, N, Zj, ldz);               // Z = U^H Zs
+            else trsm_LUN<T>(c, st, N, wj, B, ldb, 0, Zs, N, Zj, ldz, c.trsm_base);           // Z = U^-1 Zs
+        }
+        pt.end(PH_TRSM);
+        if (il > 1) {   // w_d holds all N eigenvalues: the selected ones to the front
+            double* wt = c.scratch<double>("evd_wsel", (size_t)m);
+            EIG_HIP(hipMemcpyAsync(wt, w_d + (il - 1), sizeof(double) * m, hipMemcpyDeviceToDevice, st));
+            EIG_HIP(hipMemcpyAsync(w_d, wt, sizeof(double) * m, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    c.sync(st);
+    pt.collect(PH_GST);
+    if (m > 0) { pt.collect(PH_BT); pt.collect(PH_TRSM); }
+    *meig = m;
     c.phase_ms[PH_TOTAL] = now_ms() - t_all;
     return 0;
 }
@@ -1284,5 +1394,113 @@ int eigsolve_dstedc_device(int N, const double* d_d, const double* e_d, double* 
         c.sync(c.s1);
         if (ms) *ms = now_ms() - t0;
         return r;
+    });
+}
+
+// ---- extended generalized driver (include/eigsolve_gpu.h) ----
+// The device tridiagonal solver is always used, and the real path always honours il: both options are overridden for the call.
+struct ExOptions {
+    Ctx& c;
+    int td, ril;
+    explicit ExOptions(Ctx& c_) : c(c_), td(c_.tridiag_device), ril(c_.real_il_reference) { c.tridiag_device = 1; c.real_il_reference = 0; }
+    ~ExOptions() { c.tridiag_device = td; c.real_il_reference = ril; }
+};
+
+// argument checks of the extended driver (before any device work); lwork_min / lrwork_min: the minima of eigsolve_?hegvdx
+static bool ex_args_ok(const char* name, int itype, char jobz, char range, int N, const void* A, int lda, const void* B, int ldb, double vl,
+                       double vu, int il, int iu, const int* meig, const double* w_d, const void* Z, int ldz, bool work_null, long lwork,
+                       long lwork_min, long lrwork, long lrwork_min) {
+    if (itype < 1 || itype > 3) { printf(" %s error: itype must be 1, 2 or 3\n", name); return false; }
+    if (jobz != 'N' && jobz != 'V') { printf(" %s error: jobz must be 'N' or 'V'\n", name); return false; }
+    if (range != 'A' && range != 'V' && range != 'I') { printf(" %s error: range must be 'A', 'V' or 'I'\n", name); return false; }
+    if (N <= 0 || lda < N || ldb < N || !A || !B || !meig || !w_d) { printf(" %s error: invalid N/lda/ldb or null argument\n", name); return false; }
+    if (jobz == 'V' && (!Z || ldz < N)) { printf(" %s error: jobz = 'V' needs Z_d with ldz >= N\n", name); return false; }
+    if (range == 'V' && !(vl < vu)) { printf(" %s error: range = 'V' needs vl < vu\n", name); return false; }
+    if (range == 'I' && (il < 1 || iu > N || iu < il)) { printf(" %s error: invalid il/iu\n", name); return false; }
+    if (work_null) { printf(" %s error: null workspace\n", name); return false; }
+    if (lwork < lwork_min) { printf(" %s error: lwork must be at least %ld\n", name, lwork_min); return false; }
+    if (lrwork < lrwork_min) { printf(" %s error: lrwork must be at least N\n", name); return false; }
+    return true;
+}
+
+int eigsolve_zhegvdx_ex(int itype, char jobz, char range, int N, void* A_d, int lda, void* B_d, int ldb, double vl, double vu, int il,
+                        int iu, int* meig, double* w_d, void* Z_d, int ldz, void* work_d, int lwork, double* rwork_d, int lrwork, int* info) {
+    if (meig) *meig = 0;
+    return guarded(info, [&]() -> int {
+        const long n = N;
+        if (!ex_args_ok("zhegvdx_ex_gpu", itype, jobz, range, N, A_d, lda, B_d, ldb, vl, vu, il, iu, meig, w_d, Z_d, ldz, !work_d || !rwork_d,
+                        lwork, 2 * 64 * 64 + 65 * n, lrwork, n))
+            return -1;
+        Ctx& c = ctx();
+        ExOptions ex(c);
+        cplx* work = (cplx*)work_d;   // carve-up of eigsolve_zhegvdx: tau = work(1:N), e = rwork(1:N), rest of work = panel W
+        return hegvdx_ex_core<cplx>(c, itype, jobz == 'V', range, N, (cplx*)A_d, lda, (cplx*)B_d, ldb, vl, vu, range == 'A' ? 1 : il,
+                                    range == 'A' ? N : iu, meig, w_d, (cplx*)Z_d, ldz, rwork_d, work, work + n, "zhegvdx_ex_gpu");
+    });
+}
+
+int eigsolve_dsygvdx_ex(int itype, char jobz, char range, int N, double* A_d, int lda, double* B_d, int ldb, double vl, double vu, int il,
+                        int iu, int* meig, double* w_d, double* Z_d, int ldz, double* work_d, int lwork, int* info) {
+    if (meig) *meig = 0;
+    return guarded(info, [&]() -> int {
+        const long n = N;
+        if (!ex_args_ok("dsygvdx_ex_gpu", itype, jobz, range, N, A_d, lda, B_d, ldb, vl, vu, il, iu, meig, w_d, Z_d, ldz, !work_d,
+                        lwork, 2 * 64 * 64 + 66 * n, 0, 0))
+            return -1;
+        Ctx& c = ctx();
+        ExOptions ex(c);
+        // carve-up of eigsolve_dsygvdx: e = work(1:N), tau = work(N+1:2N), W = work(2N+1:)
+        return hegvdx_ex_core<double>(c, itype, jobz == 'V', range, N, A_d, lda, B_d, ldb, vl, vu, range == 'A' ? 1 : il,
+                                      range == 'A' ? N : iu, meig, w_d, Z_d, ldz, work_d, work_d + n, work_d + 2 * n, "dsygvdx_ex_gpu");
+    });
+}
+
+template <class T> static int hegst_ex_entry(int itype, int N, T* A, int lda, const T* B, int ldb) {
+    return guarded(nullptr, [&]() -> int {
+        if (itype < 1 || itype > 3 || N < 0 || (N > 0 && (lda < N || ldb < N || !A || !B))) {
+            printf(" %s error: invalid itype/N/lda/ldb\n", Tr<T>::cx ? "zhegst_ex" : "dsygst_ex");
+            return -1;
+        }
+        if (N == 0) return 0;
+        Ctx& c = ctx();
+        if (itype == 1) {
+            build_invU<T>(c, c.s1, N, B, ldb);
+            build_inv_blocks<T>(c, c.s1, N, B, ldb);
+            hegst_upper<T>(c, c.s1, N, A, lda, B, ldb);
+        } else {
+            hegst_upper_itype23<T>(c, c.s1, N, A, lda, B, ldb);
+        }
+        c.sync(c.s1);
+        return 0;
+    });
+}
+int eigsolve_zhegst_ex(int itype, int N, void* A_d, int lda, const void* B_d, int ldb) {
+    return hegst_ex_entry<cplx>(itype, N, (cplx*)A_d, lda, (const cplx*)B_d, ldb);
+}
+int eigsolve_dsygst_ex(int itype, int N, double* A_d, int lda, const double* B_d, int ldb) {
+    return hegst_ex_entry<double>(itype, N, A_d, lda, B_d, ldb);
+}
+
+// Device bisection on (d, e): eigenvalues by range into w_d[0 : *m), ascending.  Test / bench entry point.
+int eigsolve_dstebz_device(int N, const double* d_d, const double* e_d, char range, double vl, double vu, int il, int iu, int* m,
+                           double* w_d, double* ms) {
+    if (m) *m = 0;
+    return guarded(nullptr, [&]() -> int {
+        if (N <= 0 || !d_d || (N > 1 && !e_d) || !w_d || !m || (range != 'A' && range != 'V' && range != 'I') ||
+            (range == 'V' && !(vl < vu)) || (range == 'I' && (il < 1 || iu > N || iu < il))) {
+            printf(" dstebz_device error: invalid arguments\n");
+            return -1;
+        }
+        Ctx& c = ctx();
+        c.sync(c.s1);
+        const double t0 = now_ms();
+        if (range == 'A') { il = 1; iu = N; }
+        stebz_prepare(c, c.s1, N, d_d, e_d);
+        if (range == 'V') stebz_value_range(c, c.s1, N, vl, vu, &il, &iu);
+        stebz_index(c, c.s1, N, il, iu, w_d);
+        c.sync(c.s1);
+        if (ms) *ms = now_ms() - t0;
+        *m = std::max(0, iu - il + 1);
+        return 0;
     });
 }

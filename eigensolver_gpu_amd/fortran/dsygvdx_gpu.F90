@@ -15,6 +15,15 @@ module dsygvdx_gpu
       integer(c_int), dimension(*) :: iwork_h
       integer(c_int)               :: info
     end function eigsolve_dsygvdx
+    integer(c_int) function eigsolve_dsygvdx_ex(itype, jobz, range, N, A, lda, B, ldb, vl, vu, il, iu, meig, w, Z, ldz, &
+                                                work, lwork, info) bind(C, name="eigsolve_dsygvdx_ex")
+      import :: c_int, c_ptr, c_double, c_char
+      integer(c_int), value :: itype, N, lda, ldb, il, iu, ldz, lwork
+      character(kind=c_char), value :: jobz, range
+      real(c_double), value :: vl, vu
+      type(c_ptr), value :: A, B, w, Z, work
+      integer(c_int) :: meig, info
+    end function eigsolve_dsygvdx_ex
   end interface
 
 contains
@@ -41,5 +50,20 @@ contains
                              int(liwork_h, c_int), Z_h, int(ldz_h, c_int), w_h, cinfo, skip)
     info = cinfo
   end subroutine dsygvdx_gpu
+
+  ! Extended driver (include/eigsolve_gpu.h, eigsolve_dsygvdx_ex): the real analogue of zhegvdx_ex_gpu (LAPACK DSYGVX's
+  ! arguments, UPLO = 'U'); device workspace as dsygvdx_gpu.
+  subroutine dsygvdx_ex_gpu(itype, jobz, range, N, A, lda, B, ldb, vl, vu, il, iu, meig, w, Z, ldz, work, lwork, info)
+    integer                :: itype, N, lda, ldb, il, iu, meig, ldz, lwork, info
+    character              :: jobz, range
+    real(8)                :: vl, vu
+    type(c_ptr)            :: A, B, w, Z, work          ! DEVICE pointers
+    integer(c_int) :: istat, cinfo, cm
+    cinfo = 0; cm = 0
+    istat = eigsolve_dsygvdx_ex(int(itype, c_int), jobz, range, int(N, c_int), A, int(lda, c_int), B, int(ldb, c_int), vl, vu, &
+                                int(il, c_int), int(iu, c_int), cm, w, Z, int(ldz, c_int), work, int(lwork, c_int), cinfo)
+    meig = cm
+    info = cinfo
+  end subroutine dsygvdx_ex_gpu
 
 end module dsygvdx_gpu

@@ -33,9 +33,11 @@ module lapack_host
 
 contains
 
-  ! A x = lambda B x, all eigenpairs, upper triangles: A <- eigenvectors, B <- Cholesky factor, w <- eigenvalues
-  subroutine host_zhegvd(n, a, lda, b, ldb, w, info)
+  ! A x = lambda B x (itype 2: A B x = lambda x, 3: B A x = lambda x), all eigenpairs, upper triangles: A <- eigenvectors,
+  ! B <- Cholesky factor, w <- eigenvalues
+  subroutine host_zhegvd(n, a, lda, b, ldb, w, info, itype)
     integer, intent(in) :: n, lda, ldb
+    integer, intent(in), optional :: itype
     complex(8), intent(inout) :: a(lda,*), b(ldb,*)
     real(8), intent(out) :: w(*)
     integer, intent(out) :: info
@@ -46,6 +48,7 @@ contains
     real(8) :: rq(1)
     integer(c_int) :: iq(1), cinfo, lw, lr, li, one
     one = 1
+    if (present(itype)) one = int(itype, c_int)
     lw = -1; lr = -1; li = -1
     call scipy_zhegvd(one, 'V', 'U', int(n, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, wq, lw, rq, lr, iq, li, cinfo, &
                       1_c_size_t, 1_c_size_t)
@@ -56,8 +59,9 @@ contains
     info = cinfo
   end subroutine host_zhegvd
 
-  subroutine host_dsygvd(n, a, lda, b, ldb, w, info)
+  subroutine host_dsygvd(n, a, lda, b, ldb, w, info, itype)
     integer, intent(in) :: n, lda, ldb
+    integer, intent(in), optional :: itype
     real(8), intent(inout) :: a(lda,*), b(ldb,*)
     real(8), intent(out) :: w(*)
     integer, intent(out) :: info
@@ -66,6 +70,7 @@ contains
     real(8) :: wq(1)
     integer(c_int) :: iq(1), cinfo, lw, li, one
     one = 1
+    if (present(itype)) one = int(itype, c_int)
     lw = -1; li = -1
     call scipy_dsygvd(one, 'V', 'U', int(n, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, wq, lw, iq, li, cinfo, &
                       1_c_size_t, 1_c_size_t)

@@ -21,6 +21,15 @@ module zhegvdx_gpu
       integer(c_int), dimension(*)            :: iwork_h
       integer(c_int)                          :: info
     end function eigsolve_zhegvdx
+    integer(c_int) function eigsolve_zhegvdx_ex(itype, jobz, range, N, A, lda, B, ldb, vl, vu, il, iu, meig, w, Z, ldz, &
+                                                work, lwork, rwork, lrwork, info) bind(C, name="eigsolve_zhegvdx_ex")
+      import :: c_int, c_ptr, c_double, c_char
+      integer(c_int), value :: itype, N, lda, ldb, il, iu, ldz, lwork, lrwork
+      character(kind=c_char), value :: jobz, range
+      real(c_double), value :: vl, vu
+      type(c_ptr), value :: A, B, w, Z, work, rwork
+      integer(c_int) :: meig, info
+    end function eigsolve_zhegvdx_ex
   end interface
 
 contains
@@ -51,5 +60,23 @@ contains
                              int(ldz_h, c_int), w_h, cinfo, skip)
     info = cinfo
   end subroutine zhegvdx_gpu
+
+  ! Extended driver (include/eigsolve_gpu.h, eigsolve_zhegvdx_ex): itype 1 / 2 / 3, jobz 'N' / 'V', range 'A' / 'V' / 'I'
+  ! (LAPACK ZHEGVX's ITYPE, JOBZ, RANGE, VL, VU, IL, IU, M), UPLO = 'U'.  meig eigenvalues ascending in w(1:meig), eigenvectors
+  ! in Z(:, 1:meig) for jobz = 'V' (Z may be c_null_ptr for jobz = 'N').  Device workspaces as zhegvdx_gpu, no host ones.
+  subroutine zhegvdx_ex_gpu(itype, jobz, range, N, A, lda, B, ldb, vl, vu, il, iu, meig, w, Z, ldz, work, lwork, rwork, lrwork, &
+                            info)
+    integer                :: itype, N, lda, ldb, il, iu, meig, ldz, lwork, lrwork, info
+    character              :: jobz, range
+    real(8)                :: vl, vu
+    type(c_ptr)            :: A, B, w, Z, work, rwork          ! DEVICE pointers
+    integer(c_int) :: istat, cinfo, cm
+    cinfo = 0; cm = 0
+    istat = eigsolve_zhegvdx_ex(int(itype, c_int), jobz, range, int(N, c_int), A, int(lda, c_int), B, int(ldb, c_int), vl, vu, &
+                                int(il, c_int), int(iu, c_int), cm, w, Z, int(ldz, c_int), work, int(lwork, c_int), rwork,   &
+                                int(lrwork, c_int), cinfo)
+    meig = cm
+    info = cinfo
+  end subroutine zhegvdx_ex_gpu
 
 end module zhegvdx_gpu

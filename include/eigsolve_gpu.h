@@ -123,7 +123,8 @@ void eigsolve_range_pop(void);
 /* Per-phase wall times (ms) of the LAST driver call on this thread/device, measured with
  * HIP events on the library's stream plus a host clock for the host LAPACK step:
  * [0] potrf [1] gst [2] trd total [3] host stedc (+ D2H d,e / H2D vectors) [4] back-transform
- * [5] trsm [6] final D2H copy [7] total.  Returns the number of entries written (<= n). */
+ * [5] trsm [6] final D2H copy [7] total.  Returns the number of entries written (<= n).
+ * Extended drivers: [3] holds the bisection for jobz = 'N', [5] the final trmm for itype 3. */
 int eigsolve_get_phase_times(double *ms, int n);
 
 /* ---- drivers (the drop-in boundary) -------------------------------------------------- */
@@ -148,6 +149,27 @@ int eigsolve_zhegvdx(int N, void *A_d, int lda, void *B_d, int ldb, void *Z_d, i
 int eigsolve_dsygvdx(int N, double *A_d, int lda, double *B_d, int ldb, double *Z_d, int ldz, int il, int iu,
                      double *w_d, double *work_d, int lwork, double *work_h, int lwork_h, int *iwork_h,
                      int liwork_h, double *Z_h, int ldz_h, double *w_h, int *info, int skip_host_copy);
+
+/* Extended generalized driver (LAPACK ?hegvx / ?sygvd, cuSOLVER ?sygvdx):
+ *   itype 1: A x = lambda B x,  2: A B x = lambda x,  3: B A x = lambda x;  jobz 'N' (eigenvalues only) / 'V';
+ *   range 'A' (all), 'V' (the eigenvalues in (vl, vu], vl < vu), 'I' (il..iu, 1 <= il <= iu <= N).
+ * Upper triangles of A_d, B_d, column-major.  Device workspace minima as eigsolve_zhegvdx / eigsolve_dsygvdx (lwork, lrwork);
+ * no host workspaces; the tridiagonal step always runs on the device.  Blocking: results are valid on return.  On exit:
+ * *meig = number of eigenpairs selected; w_d[0 : meig) their eigenvalues ascending (LAPACK ?hegvx's W(1:M)), the rest of w_d
+ * unspecified; jobz = 'V': Z_d(:, 0 : meig) the eigenvectors, normalised as LAPACK does (Z^H B Z = I for itype 1 and 2,
+ * Z^H B^-1 Z = I for itype 3); Z_d needs N columns for range 'V', meig otherwise, and may be NULL for jobz = 'N'.  B_d holds U
+ * (B = U^H U), upper(A_d) is destroyed, strict lower(A_d) is preserved.  *info = 0 ok / -1 with a message: bad itype, jobz,
+ * range, N, leading dimension, range bounds or workspace (detected before any device work: A_d, B_d unmodified), or B not
+ * positive definite.  range 'V': an eigenvalue within O(eps ||T||) of vl or vu may be counted on either side of it (as LAPACK
+ * ?stebz).  itype 1, jobz 'V', range 'I' / 'A' runs the launches of eigsolve_zhegvdx with "tridiag" = 1: Z and w_d[0 : meig)
+ * are bit-identical to its Z and w(il:iu).  Fortran: zhegvdx_ex_gpu / dsygvdx_ex_gpu in modules zhegvdx_gpu / dsygvdx_gpu. */
+int eigsolve_zhegvdx_ex(int itype, char jobz, char range, int N, void *A_d, int lda, void *B_d, int ldb, double vl, double vu,
+                        int il, int iu, int *meig, double *w_d, void *Z_d, int ldz, void *work_d, int lwork, double *rwork_d,
+                        int lrwork, int *info);
+/* Real analogue: lwork >= 2*64*64+66*N, no rwork. */
+int eigsolve_dsygvdx_ex(int itype, char jobz, char range, int N, double *A_d, int lda, double *B_d, int ldb, double vl,
+                        double vu, int il, int iu, int *meig, double *w_d, double *Z_d, int ldz, double *work_d, int lwork,
+                        int *info);
 
 /* Batch of nprob problems of ONE order (QE k-point style, BASELINE.json configs[4]) solved by one call from one host thread.
  * The library keeps "batch_workers" (automatic: 3, or 4 with GPU_MAX_HW_QUEUES >= 5) of the problems in flight on its own
@@ -185,6 +207,10 @@ int eigsolve_dsyevd(int il, int iu, int N, double *A_d, int lda, double *Z_d, in
  * blocking).  Only the upper triangle of A is read or written. */
 int eigsolve_zhegst(int N, void *A_d, int lda, const void *B_d, int ldb, int nb);
 int eigsolve_dsygst(int N, double *A_d, int lda, const double *B_d, int ldb, int nb);
+/* LAPACK ?hegst, uplo='U', B_d holds U: itype 1 A <- U^-H A U^-1 (eigsolve_zhegst), itype 2 / 3 A <- U A U^H (two MFMA
+ * products).  Only the upper triangle of A is read or written.  Returns 0 / -1 (bad itype, N, lda, ldb). */
+int eigsolve_zhegst_ex(int itype, int N, void *A_d, int lda, const void *B_d, int ldb);
+int eigsolve_dsygst_ex(int itype, int N, double *A_d, int lda, const double *B_d, int ldb);
 
 /* zhetrd_gpu / dsytrd_gpu (zhetrd_gpu.F90:30-96): uplo='U'.  d[N], e[N-1], tau[N-1] device
  * outputs; reflectors in upper(A) exactly as the reference leaves them (explicit 1 at
@@ -277,6 +303,12 @@ int eigsolve_dtrsm_lun(int N, int m, const double *U_d, int ldu, double *Z_d, in
  * replacing the host zstedc/dstedc('I') of zheevd_gpu.F90:101.  w_d[N] ascending, Q_d (N x N, ldq)
  * eigenvectors (may be NULL), *ms host wall time.  d_d/e_d are not modified (w_d may alias d_d). */
 int eigsolve_dstedc_device(int N, const double *d_d, const double *e_d, double *w_d, double *Q_d, int ldq, double *ms);
+
+/* Device bisection for the symmetric tridiagonal (d_d[N], e_d[N-1]): LAPACK dstebz with abstol = 0, range 'A', 'V' ((vl, vu])
+ * or 'I' (il..iu).  *m = number found, w_d[0 : *m) ascending; every value depends only on (d, e, its index).  *ms host wall
+ * time.  d_d/e_d are not modified.  Returns 0 / -1 (bad arguments). */
+int eigsolve_dstebz_device(int N, const double *d_d, const double *e_d, char range, double vl, double vu, int il, int iu, int *m,
+                           double *w_d, double *ms);
 
 /* Library version / build info string. */
 const char *eigsolve_version(void);
